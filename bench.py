@@ -7,7 +7,15 @@ The docs are generated in HBM by the device port of the deterministic generator
 (tokenizer-zig_amd/csrc/gen.hip, byte-identical to synth.cpp): a rank stages nothing on
 the host.
 
-Every region is verified in the same run (verdict r2 item 1a): the rolling hashes of
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline figure needs: it
+builds the tables and the inputs, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`, the step's roofline from the kernel timers of those same steps).
+`--dump-outputs DIR` adds the last timed step's result as .npy files (dump_outputs).
+Everything else described below (verification against the oracle, the memo-off, two-stream,
+decode, pad, host-buffer and single-doc regions, the secondary configs, the CPU baseline,
+the PMC and trace citations) runs under `--full` only.
+
+`--full`: every region is verified in the same run (verdict r2 item 1a): the rolling hashes of
 the whole device result (row_ptr, ids, offsets; computed on the device) against the C++
 oracle's hashes of the same shard committed under tests/golden/, plus a doc-by-doc
 comparison of a bounded sample with the oracle run here. Any mismatch on any rank makes
@@ -21,7 +29,7 @@ parent spawns N fresh child processes before anything touches HIP, relays rank 0
 line and exits non-zero if any rank fails. A gloo barrier brackets each timed region and
 the max time over ranks is reported. rank 0 prints one JSON line: the C1 value with its
 roofline (algorithmic bytes of the step / step time, HIP events on the
-encode stream), the memo-off and two-stream rates, the secondary regions (C2, C3, C5,
+encode stream) and, under `--full`, the memo-off and two-stream rates, the secondary regions (C2, C3, C5,
 C6 at 1M docs per rank, C4 at its BASELINE per-GPU shard of 8M docs), and `cpu_baseline`
 (the C++ restatement of the reference's CPU algorithm on a bounded sample; N=1 only).
 """
@@ -86,6 +94,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also verify every region against the oracle and run the memo-off, two-stream, decode, "
+                         "pad, host-buffer, single-doc and secondary regions and the CPU baseline (each has its "
+                         "own --no-* flag below); without it only the primary region is timed")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's result (row_ptr, and the ids and offsets of "
+                         "a seeded sample of docs) as DIR/<name>.npy in float64")
     ap.add_argument("--config", type=int, default=1,
                     help="0..4 = BASELINE.json configs, 5 = C1 on a disjoint lexicon, 6 = C1 under ByteLevel, "
                          "7 = C1 under a 106k-id vocab, 8 = C1 + unk under Metaspace, 9 = C7 under ByteLevel")
@@ -114,7 +129,7 @@ def parse_args(argv=None):
                     help="batches in flight: step k runs batch k %% S on HIP stream k %% S (each batch its own "
                          "workspace and outputs over the same resident input); 0 = 2 when two one-pass batches "
                          "fit in free HBM, else 1")
-    ap.add_argument("--verify", action="store_true", help="(default; kept for older command lines)")
+    ap.add_argument("--verify", action="store_true", help="(the default under --full; kept for older command lines)")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle sample and the hash check")
     ap.add_argument("--verify-docs", type=int, default=100_000, help="oracle sample of the primary region")
     ap.add_argument("--no-memo", action="store_true", help="disable the BPE word memo (vocab-key results)")
@@ -127,6 +142,15 @@ def parse_args(argv=None):
     ap.add_argument("--simulate-cpu", action="store_true",
                     help="test only: each rank runs the C++ oracle as its step (no GPU; the multi-rank harness on CPU)")
     return ap.parse_args(argv)
+
+
+def plain_run(args):
+    """Without --full only the primary region runs: every other region, the verification
+    and the CPU baseline are switched off through their own flags."""
+    if not args.full:
+        args.no_verify = args.no_memo_off_run = args.no_pipelined_run = args.primary_only = True
+        args.no_cpu_baseline = args.no_host_e2e = args.no_single_doc = args.no_decode_pad = True
+    return args
 
 
 def default_docs(cfg):
@@ -441,6 +465,64 @@ def two_batches_fit(tok, total: int, n_docs: int) -> bool:
         return False
     one = int(tkz.lib().tkz_device_workspace_size(tok.handle, total, n_docs)) + 13 * total + 16 * (n_docs + 2) + 64
     return 2 * one <= 0.9 * free.value
+
+
+# --------------------------------------------------------------------------- outputs
+DUMP_SEED = 20240607
+DUMP_ROW_ENTRIES = 2_000_000  # row_ptr entries written (16 MB as float64)
+DUMP_TOKENS = 1_500_000  # tokens of the sampled docs written (36 MB: ids + 2 offsets, float64 each)
+
+
+def dump_outputs(tkz, db, out_dir, rank=0):
+    """What a caller of the timed path receives from its last step (DeviceBatch.results: the
+    CSR row_ptr, ids, offsets), as out_dir/<name>.npy in float64 (every value is an integer
+    below 2^53, so exact), at most 64 MB in all:
+      totals.npy     [n_docs, n_tokens]
+      row_ptr.npy    the whole row_ptr (n_docs + 1 entries) when it has at most DUMP_ROW_ENTRIES,
+                     else its entries at a sorted seeded sample of that many positions
+      doc_index.npy  a sorted seeded sample of docs (the first docs of a seeded permutation whose
+                     tokens fit in DUMP_TOKENS; at least one doc)
+      doc_rows.npy   [k, 2] row_ptr[d], row_ptr[d + 1] of those docs
+      ids.npy        their ids, concatenated in doc order
+      offsets.npy    [tokens, 2] their offsets
+    The sample depends only on DUMP_SEED and n_docs and on row_ptr itself, so two builds that
+    compute the same result write the same files. Ranks above 0 prefix the names with
+    rank<r>_. Returns the file names and the bytes written."""
+    db.sync()
+    st = db.status()
+    if st:
+        raise tkz.TokenizerError(st, "device-reported error")
+    L = tkz.lib()
+    n = db.n_docs
+    row = np.zeros(n + 1, dtype=np.uint64)
+    db.d_row.download(row)
+    rng = np.random.default_rng(DUMP_SEED)
+    pos = np.arange(n + 1) if n + 1 <= DUMP_ROW_ENTRIES else np.sort(rng.choice(n + 1, DUMP_ROW_ENTRIES, replace=False))
+    perm = rng.permutation(n)
+    counts = np.diff(row.astype(np.int64))
+    k = max(1, int(np.searchsorted(np.cumsum(counts[perm]), DUMP_TOKENS, side="right"))) if n else 0
+    docs = np.sort(perm[:k])
+    t0 = row[docs].astype(np.int64)
+    cnt = np.minimum(counts[docs], DUMP_TOKENS)  # (a single doc above the budget: its first tokens)
+    dst = np.zeros(len(docs) + 1, dtype=np.int64)
+    dst[1:] = np.cumsum(cnt)
+    ids = np.zeros(max(int(dst[-1]), 1), dtype=np.uint32)
+    offs = np.zeros((max(int(dst[-1]), 1), 2), dtype=np.uint32)
+    for a, c, d in zip(t0.tolist(), cnt.tolist(), dst.tolist()):
+        if c and (L.tkz_memcpy_dtoh(ctypes.c_void_p(ids.ctypes.data + d * 4), db.d_ids.ptr + a * 4, c * 4) or
+                  L.tkz_memcpy_dtoh(ctypes.c_void_p(offs.ctypes.data + d * 8), db.d_offs.ptr + a * 8, c * 8)):
+            raise RuntimeError("tkz_memcpy_dtoh failed")
+    arrays = {"totals": np.array([n, int(row[-1])]), "row_ptr": row[pos], "doc_index": docs,
+              "doc_rows": np.stack([row[docs], row[docs + 1]], axis=1) if len(docs) else np.zeros((0, 2)),
+              "ids": ids[:int(dst[-1])], "offsets": offs[:int(dst[-1])]}
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if rank else ""
+    nbytes = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+        nbytes += a.nbytes
+    return {"dir": out_dir, "files": [prefix + k + ".npy" for k in arrays], "bytes": nbytes}
 
 
 # --------------------------------------------------------------------------- verification
@@ -831,7 +913,9 @@ def host_e2e_region(tkz, synth, dist, cfg, n_docs, args):
 # --------------------------------------------------------------------------- main
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    args = parse_args(argv)
+    args = plain_run(parse_args(argv))
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch(argv, args.gpus))
     if args.simulate_cpu:
@@ -876,6 +960,9 @@ def main(argv=None):
     tkz.profile_enable(tok, False)
     stats = db.stats()
     n_tokens = db.n_tokens()
+    dumped = None
+    if args.dump_outputs:  # the batch the last timed step wrote (step k runs batch k % S)
+        dumped = dump_outputs(tkz, dbs[(args.warmup + args.steps - 1) % len(dbs)], args.dump_outputs, dist.rank)
     ver = None
     if not args.no_verify:
         ver = verify_region(cfg, js, db, first, args.verify_docs, dist.world,
@@ -931,7 +1018,7 @@ def main(argv=None):
     enc_s = per_call(ms_enc) / 1e3
     comp_s = per_call(ms_comp) / 1e3
     src_hash = kernel_src_hash()
-    default_cmd = cfg == 1 and not args.no_memo and n_docs == default_docs(cfg) and max_ws is None
+    default_cmd = args.full and cfg == 1 and not args.no_memo and n_docs == default_docs(cfg) and max_ws is None
     pmc_file, pmc = pmc_summary(src_hash) if default_cmd else (None, {})
     trace_file, trace_ms = trace_summary(src_hash) if default_cmd else (None, None)
     step_pmc = pmc.get("step", {})
@@ -1023,6 +1110,8 @@ def main(argv=None):
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "u8",
+        "full": args.full,
+        "outputs": dumped,
         "data": "synthetic (deterministic generator, generated in HBM by tokenizer-zig_amd/csrc/gen.hip = "
                 "synth.cpp; vocab trained in-repo)",
         "config": {"workload": WORKLOADS[cfg], "docs_per_gpu": n_docs, "bytes_per_gpu": total,
@@ -1075,7 +1164,8 @@ def main_simulated(args):
     first_all = [dist.sum(float(shard_first_doc(dist.rank, n_docs)) if r == dist.rank else 0.0)
                  for r in range(dist.world)]
     out = {"metric": METRIC, "value": round(total_all * args.steps / el / 1e6, 3), "unit": "MB/s",
-           "n_gpus": dist.world, "steps": args.steps, "warmup": args.warmup, "simulated_cpu": True,
+           "n_gpus": dist.world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(el / args.steps * 1e3, 3), "simulated_cpu": True,
            "config": {"bytes_all": int(total_all), "tokens_all": int(tokens_all), "shard_first_docs": first_all,
                       "parallelism": f"doc-shard x{dist.world}"}}
     dist.close()

@@ -1,5 +1,6 @@
 """Workspace-bounded device encode (doc-aligned sub-batches), the batch statistics, the
-C4 shard at its BASELINE size, and the multi-rank bench on one GPU.
+C4 shard at its BASELINE size, the multi-rank bench on one GPU, and the plain bench run's
+output files.
 
 A batch whose one-pass workspace exceeds the caller's runs in sub-batches; the outputs
 must be identical to the oracle's (and so to a one-pass run) whatever the cut points."""
@@ -220,7 +221,7 @@ def test_bench_two_ranks_share_gpu():
     """bench.py --gpus 2 (no torchrun) on one GPU: two HIP ranks, each encoding and
     verifying its own shard against the oracle; one JSON line with both shards."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--share-gpu",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--share-gpu",
                         "--docs", "50000", "--steps", "2", "--warmup", "1", "--verify", "--verify-docs", "50000",
                         "--no-cpu-baseline", "--no-memo-off-run", "--primary-only"], capture_output=True, text=True,
                        timeout=300, env=env)
@@ -231,3 +232,44 @@ def test_bench_two_ranks_share_gpu():
     assert (v["docs_per_rank"], v["sample_match"], v["ranks_failed"]) == (50000, True, 0)
     assert out["config"]["parallelism"] == "doc-shard x2"
     assert out["config"]["bytes_per_gpu"] == 50000 * 512
+
+
+def test_bench_plain_run_dumps_last_step(tmp_path, monkeypatch):
+    """A plain `bench.py --steps K --warmup W --dump-outputs DIR` (no --full): no region but
+    the primary one runs, and the files hold what the timed path returned: the whole row_ptr
+    and the ids / offsets of the sampled docs equal DeviceBatch.results() of the same docs,
+    and a second run writes the same bytes."""
+    import bench
+
+    argv = ["--config", "2", "--docs", "3001", "--steps", "2", "--warmup", "1", "--dump-outputs"]
+    out = bench.main(argv + [str(tmp_path / "a")])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["full"] is False
+    assert out["verified"] is None and out["secondary"] is None and out["cpu_baseline"] is None
+    assert out["memo"]["memo_off"] is None and out["pipelined"] is None and out["host_e2e"] is None
+    d = {f[:-4]: np.load(tmp_path / "a" / f) for f in out["outputs"]["files"]}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert sum(a.nbytes for a in d.values()) == out["outputs"]["bytes"] <= 64 << 20
+    tok = tkz.Tokenizer.from_json(synth.tokenizer_json(2))
+    data, off = synth.docs(2, 3001)
+    (row, ids, offs), _ = _device(tok, data, off)
+    assert d["totals"].tolist() == [3001, len(ids)]
+    assert np.array_equal(d["row_ptr"], row)
+    docs = d["doc_index"].astype(np.int64)
+    assert len(docs) == 3001 and np.array_equal(docs, np.arange(3001))  # every doc fits the token budget
+    assert np.array_equal(d["doc_rows"], np.stack([row[:-1], row[1:]], axis=1))
+    assert np.array_equal(d["ids"], ids) and np.array_equal(d["offsets"], offs)
+    bench.main(argv + [str(tmp_path / "b")])
+    for f in out["outputs"]["files"]:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    # a result above the budgets: a sample of row_ptr entries, whole docs up to the token budget
+    monkeypatch.setattr(bench, "DUMP_ROW_ENTRIES", 1000)
+    monkeypatch.setattr(bench, "DUMP_TOKENS", 5000)
+    out = bench.main(argv + [str(tmp_path / "c")])
+    s = {f[:-4]: np.load(tmp_path / "c" / f) for f in out["outputs"]["files"]}
+    assert len(s["row_ptr"]) == 1000 and np.all(np.diff(s["row_ptr"]) >= 0) and np.isin(s["row_ptr"], row).all()
+    docs = s["doc_index"].astype(np.int64)
+    assert 0 < len(docs) < 3001 and np.all(np.diff(docs) > 0)
+    assert np.array_equal(s["doc_rows"], np.stack([row[docs], row[docs + 1]], axis=1))
+    sel = np.concatenate([np.arange(int(row[i]), int(row[i + 1])) for i in docs])
+    assert 5000 - 512 < len(sel) <= 5000  # (a 512-B doc has at most 512 tokens)
+    assert np.array_equal(s["ids"], ids[sel]) and np.array_equal(s["offsets"], offs[sel])

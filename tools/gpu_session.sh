@@ -15,7 +15,7 @@ if [ -z "$SKIP_TESTS" ]; then
     > $D/pytest.log 2>&1 || { tail -30 $D/pytest.log; exit 1; }
   tail -1 $D/pytest.log
 fi
-timeout -k 10 900 python3 bench.py > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$R/$D/trace" -o run --output-format csv -- \
   python3 "$R/bench.py" $PRIMARY > "$R/$D/trace.log" 2>&1 || { tail -20 "$R/$D/trace.log"; exit 1; }

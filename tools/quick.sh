@@ -10,6 +10,7 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -1 gpurun_out/pytest_${TAG}.log
 fi
 [ $# -eq 0 ] && set -- 1 2 3 4
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the primary region verified (the other regions stay off below)
 for c in "$@"; do
   timeout -k 10 300 python3 bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --primary-only ${BENCH_ARGS} > gpurun_out/q_${TAG}_c$c.json 2> gpurun_out/q_${TAG}_c$c.err || { tail -20 gpurun_out/q_${TAG}_c$c.err; exit 1; }
   python3 -c "import json;d=json.load(open('gpurun_out/q_${TAG}_c$c.json'));k=d['roofline']['kernels'];print('C$c', round(d['value']/1e3,1), 'GB/s', d['ms_per_step'], 'ms/step', 'k_encode', k['k_encode']['avg_launch_ms'], k['other_ms'], 'verified', d['verified'] and d['verified']['sample_match'])"

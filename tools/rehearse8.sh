@@ -7,7 +7,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=${TAG:-r04r}; D=gpurun_out/$TAG; mkdir -p $D
 t0=$(date +%s)
-timeout -k 10 1100 python3 bench.py --gpus 8 --share-gpu --max-workspace-gb 3 \
+timeout -k 10 1100 python3 bench.py --full --gpus 8 --share-gpu --max-workspace-gb 3 \
   --secondary 2:1000000,3:1000000,5:1000000,4:1000000,6:1000000,7:1000000 \
   > $D/bench8.json 2> $D/bench8.err || { tail -30 $D/bench8.err; exit 1; }
 echo "wall_s $(( $(date +%s) - t0 ))" | tee $D/bench8_wall.txt
