@@ -149,6 +149,16 @@ __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
     } while (0)
 
+// A block's barrier (k_encode_blk, k_bpe_short's shared queues): orders the block's LDS traffic only. __syncthreads() is also a
+// workgroup release of global memory (s_waitcnt vmcnt(0)): every barrier waited for the
+// wave's outstanding record / token stores of the previous phase
+#define EB_SYNC()                                                         \
+    do {                                                                  \
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");   \
+        __builtin_amdgcn_s_barrier();                                     \
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");   \
+    } while (0)
+
 // debug build (-DTKZ_PHASES): per-phase s_memtime cycles of k_encode, summed over waves
 #ifdef TKZ_PHASES
 #define PH_BEGIN() uint64_t ph_t0 = __builtin_amdgcn_s_memtime()
@@ -438,14 +448,45 @@ __device__ __forceinline__ uint32_t mid_tok(uint32_t id, uint32_t s, uint32_t e)
 // round trip: loads under per-pair branches were each preceded by a full vmcnt drain.
 // Compact table: cuckoo, both candidate buckets of every pair loaded together, so no
 // lane ever walks a chain.
-template <int W, bool COMPACT, bool PACK>
-__device__ __forceinline__ void reg_probe(const DevTables& T, RegWord<W, COMPACT, PACK>& w, uint32_t mask) {
+// OV (compact table, k_bpe_short / k_bpe_deferred): ov is the table's overflow bitmap in
+// LDS (DevTables::seg_over: bit b1 set iff some key whose first bucket is b1 sits in its
+// second). Every pair loads its first bucket; its second load goes to the second bucket
+// only where the first bucket's bit is set, and to bucket 0 (one line for the whole wave)
+// elsewhere: the same load instructions as the two-bucket probe, fewer distinct lines.
+// (The second loads under a wave-uniform __ballot test were measured and not kept: DESIGN §13.4.)
+__device__ __forceinline__ bool over_bit(const uint32_t* ov, uint32_t b1) {
+    return (ov[b1 >> 5] >> (b1 & 31u)) & 1u;
+}
+template <int W, bool COMPACT, bool PACK, bool OV = false>
+__device__ __forceinline__ void reg_probe(const DevTables& T, RegWord<W, COMPACT, PACK>& w, uint32_t mask,
+                                          const uint32_t* ov = nullptr) {
+    static_assert(!OV || COMPACT, "one-bucket probes: the compact table only");
     constexpr int PG = W <= 8 ? TKZ_PG : 4;
     uint32_t retry = 0;  // (wide) pairs whose home slot holds another key
 #pragma unroll
     for (int g = 0; g < W - 1; g += PG) {
         if (((mask >> g) & ((1u << PG) - 1)) == 0) continue;
-        if (COMPACT || PACK) {  // (PACK && !COMPACT: the mid table)
+        if (OV) {
+            uint4 p[PG], q[PG];
+            uint32_t h1[PG], two = 0;
+#pragma unroll
+            for (int k = g; k < g + PG && k < W - 1; ++k) {
+                const uint32_t key = (w.idv(w.sy[k]) << 16) | w.idv(w.sy[k + 1]);
+                const bool on = (mask >> k) & 1u;
+                h1[k - g] = on ? merge_bucket1_compact(key, T.m_bits) : 0u;
+                p[k - g] = cuckoo_bucket<true>(T, h1[k - g]);
+                two |= ((uint32_t)on & (uint32_t)over_bit(ov, h1[k - g])) << (k - g);
+            }
+#pragma unroll
+            for (int k = g; k < g + PG && k < W - 1; ++k) {
+                const uint32_t key = (w.idv(w.sy[k]) << 16) | w.idv(w.sy[k + 1]);
+                const bool t2 = (two >> (k - g)) & 1u;
+                q[k - g] = cuckoo_bucket<true>(T, t2 ? merge_bucket2_compact(key, T.m_bits, h1[k - g]) : 0u);
+            }
+#pragma unroll
+            for (int k = g; k < g + PG && k < W - 1; ++k)
+                if ((mask >> k) & 1u) w.pr[k] = cuckoo_match<true>(p[k - g], q[k - g], w.idv(w.sy[k]), w.idv(w.sy[k + 1]));
+        } else if (COMPACT || PACK) {  // (PACK && !COMPACT: the mid table)
             uint4 p[PG], q[PG];
 #pragma unroll
             for (int k = g; k < g + PG && k < W - 1; ++k) {
@@ -500,8 +541,10 @@ __device__ __forceinline__ void reg_probe(const DevTables& T, RegWord<W, COMPACT
 #ifndef TKZ_PROBE3
 #define TKZ_PROBE3 1  // bit 0: W = 16 (k_bpe_deferred), bit 1: W <= 8 (k_encode buckets; spills 12 B there)
 #endif
-template <int W, bool COMPACT, bool PACK>
-__device__ __forceinline__ void reg_probe_adj(const DevTables& T, RegWord<W, COMPACT, PACK>& w, int k0, uint32_t m) {
+template <int W, bool COMPACT, bool PACK, bool OV = false>
+__device__ __forceinline__ void reg_probe_adj(const DevTables& T, RegWord<W, COMPACT, PACK>& w, int k0, uint32_t m,
+                                              const uint32_t* ov = nullptr) {
+    static_assert(!OV || COMPACT, "one-bucket probes: the compact table only");
     uint32_t x0 = 0, x1 = 0, x2 = 0;
 #pragma unroll
     for (int j = 0; j < W - 1; ++j) {
@@ -510,7 +553,24 @@ __device__ __forceinline__ void reg_probe_adj(const DevTables& T, RegWord<W, COM
         x1 = c ? w.sy[j + 1] : x1;
         if (j + 2 < W) x2 = c ? w.sy[j + 2] : x2;
     }
-    if (COMPACT || PACK) {  // (PACK && !COMPACT: the mid table)
+    if (OV) {  // first buckets, and the second ones where the bitmap sends a lane (reg_probe)
+        x0 = w.idv(x0);
+        x1 = w.idv(x1);
+        x2 = w.idv(x2);
+        const uint32_t ka = (x0 << 16) | x1, kb = (x1 << 16) | x2;
+        const bool oa = m & 1u, ob = (m >> 1) & 1u;
+        const uint32_t a1 = merge_bucket1_compact(ka, T.m_bits), b1 = ob ? merge_bucket1_compact(kb, T.m_bits) : 0u;
+        const uint4 p0 = cuckoo_bucket<true>(T, a1), p1 = cuckoo_bucket<true>(T, b1);
+        const bool ta = over_bit(ov, a1), tb = (uint32_t)ob & (uint32_t)over_bit(ov, b1);
+        const uint4 q0 = cuckoo_bucket<true>(T, ta ? merge_bucket2_compact(ka, T.m_bits, a1) : 0u);
+        const uint4 q1 = cuckoo_bucket<true>(T, tb ? merge_bucket2_compact(kb, T.m_bits, b1) : 0u);
+        const uint32_t va = cuckoo_match<true>(p0, q0, x0, x1), vb = cuckoo_match<true>(p1, q1, x1, x2);
+#pragma unroll
+        for (int j = 0; j < W - 1; ++j) {
+            if (oa && j == k0) w.pr[j] = va;
+            if (ob && j == k0 + 1) w.pr[j] = vb;
+        }
+    } else if (COMPACT || PACK) {  // (PACK && !COMPACT: the mid table)
         x0 = w.idv(x0);
         x1 = w.idv(x1);
         x2 = w.idv(x2);
@@ -607,11 +667,11 @@ __device__ __forceinline__ bool reg_init(const DevTables& T, const uint32_t* byt
 // that merged its last symbol (RE) and its first symbol (LE), in round order -- go to prof
 // as pairs (prof[k] = RE_k | LE_k << 32; SegEdges); returns the number of rounds, and in
 // *edges the list lengths (LE bits 0..7, RE bits 8..15).
-template <int W, bool COMPACT, bool PROF = false, bool PACK = COMPACT>
+template <int W, bool COMPACT, bool PROF = false, bool PACK = COMPACT, bool OV = false>
 __device__ __forceinline__ uint32_t reg_rounds(const DevTables& T, RegWord<W, COMPACT, PACK>& w, uint64_t* prof = nullptr,
-                               uint32_t* edges = nullptr) {
+                               uint32_t* edges = nullptr, const uint32_t* ov = nullptr) {
     uint32_t n_rounds = 0, lle = 0, lre = 0;
-    if (w.n >= 2) reg_probe<W, COMPACT>(T, w, (1u << (w.n - 1)) - 1);
+    if (w.n >= 2) reg_probe<W, COMPACT, PACK, OV>(T, w, (1u << (w.n - 1)) - 1, ov);
 #if TKZ_ABLATE == 2
     return 0;
 #endif
@@ -682,12 +742,12 @@ __device__ __forceinline__ uint32_t reg_rounds(const DevTables& T, RegWord<W, CO
             const int k0 = dm ? __builtin_ctz(dm) : 0;
             const uint32_t m = dm >> k0;
             if (m <= 3u) {  // one merge: its (at most two) neighbouring pairs
-                if (m) reg_probe_adj<W, COMPACT>(T, w, k0, m);
+                if (m) reg_probe_adj<W, COMPACT, PACK, OV>(T, w, k0, m, ov);
             } else {
-                reg_probe<W, COMPACT>(T, w, dm);
+                reg_probe<W, COMPACT, PACK, OV>(T, w, dm, ov);
             }
         } else {
-            reg_probe<W, COMPACT>(T, w, dm);
+            reg_probe<W, COMPACT, PACK, OV>(T, w, dm, ov);
         }
     }
     if (PROF) *edges = lle | (lre << 8);
@@ -972,16 +1032,16 @@ __device__ __forceinline__ void bpe_long_word(const DevTables& T, const uint32_t
 // lane of a converged wave (act: the lane has a word; the token counts and dense slots are
 // committed for the wave together). Returns false (nothing written) when the lane's word
 // has more than W symbols.
-template <int W, int NW, bool COMPACT>
+template <int W, int NW, bool COMPACT, bool OV = false>
 __device__ __forceinline__ bool bpe_reg_word(const DevTables& T, const uint32_t* byte_id, const uint8_t* bytes,
                                              const WordBytes<NW>& wb, uint64_t pos, uint64_t ws, uint32_t L,
-                                             const Scratch& S, bool act) {
+                                             const Scratch& S, bool act, const uint32_t* ov = nullptr) {
     RegWord<W, COMPACT> rw;
     // every caller has L <= 8 * NW: the general (multi-byte) path reads its bytes from wb
     // too (a GlbReader here cost one dependent global load per byte); no word: 0 symbols
     const bool fits = reg_init<W, COMPACT, NW>(T, byte_id, rw, wb, wb, act ? L : 0u);
 #if TKZ_ABLATE != 3
-    if (fits) reg_rounds<W, COMPACT>(T, rw);
+    if (fits) reg_rounds<W, COMPACT, false, COMPACT, OV>(T, rw, nullptr, nullptr, ov);
 #endif
     const bool emit = act && fits;
     const uint32_t c = emit ? (uint32_t)rw.n : 0u;
@@ -1191,14 +1251,26 @@ __device__ __forceinline__ void memo_lookup2(const DevTables& T, bool pa, uint64
     }
 }
 
-template <int W, int NW, bool COMPACT>
+template <int W, int NW, bool COMPACT, bool OV = false>
 __device__ __forceinline__ void bpe_bucket_word(const DevTables& T, const uint32_t* byte_id, const uint8_t* bytes,
                                                 uint64_t limit, uint64_t pos, uint64_t ws, uint32_t L,
-                                                const Scratch& S, bool act) {
+                                                const Scratch& S, bool act, const uint32_t* ov = nullptr) {
     WordBytes<NW> wb;
     wb.load(bytes, pos, limit, T.norm);
-    if (!bpe_reg_word<W, NW, COMPACT>(T, byte_id, bytes, wb, pos, ws, L, S, act) && act)
+    if (!bpe_reg_word<W, NW, COMPACT, OV>(T, byte_id, bytes, wb, pos, ws, L, S, act, ov) && act)
         bpe_long_word<COMPACT>(T, byte_id, bytes, pos, ws, L, S);  // > W symbols (rare): its own count
+}
+
+// The same for a word of <= 8 B whose normalized bytes the short list carries (k0, zero
+// past L): no load of the input bytes
+template <int W, bool COMPACT, bool OV>
+__device__ __forceinline__ void bpe_keyed_word(const DevTables& T, const uint32_t* byte_id, const uint8_t* bytes,
+                                               uint64_t k0, uint64_t pos, uint64_t ws, uint32_t L, const Scratch& S,
+                                               bool act, const uint32_t* ov) {
+    WordBytes<1> wb;
+    wb.w[0] = k0;
+    if (!bpe_reg_word<W, 1, COMPACT, OV>(T, byte_id, bytes, wb, pos, ws, L, S, act, ov) && act)
+        bpe_long_word<COMPACT>(T, byte_id, bytes, pos, ws, L, S);  // > W symbols: from the input bytes
 }
 
 // WordPiece.tokenize of one word into its record; returns its token count (the caller
@@ -1372,8 +1444,7 @@ struct Deferred {
     uint32_t* fcnt;             // [0] entries in flist, [1] (k_bpe_long's ticket over it)
     unsigned long long* seg_words;  // long words the segmented path encoded (all sub-batches)
     unsigned long long* long_bytes; // bytes of the long words k_bpe_long ran on (all sub-batches)
-    uint64_t* slist;            // k_encode_blk's memo misses of <= 8 B (k_bpe_short): chunk c's at [c << ch_log2..)
-    uint32_t* scnt;             // per chunk: its entries in slist
+    uint32_t* scnt;             // per chunk: k_encode_blk's memo misses of <= 8 B (its short_rec records, k_bpe_short)
 };
 
 // normalized bytes of a word of L <= 32 bytes, zero past L
@@ -1501,11 +1572,21 @@ __global__ __launch_bounds__(256) void k_dedup_copy(Scratch S, Deferred D) {
 #ifndef TKZ_DEF_MINB
 #define TKZ_DEF_MINB 4
 #endif
-template <bool COMPACT>
+// The word-level BPE's one-bucket probes (reg_probe's OV): the merge table's overflow bitmap
+// staged in LDS, as the segmented path's kernels do (seg_over_stage / seg_over_lds below)
+#ifndef TKZ_BPE_OVER
+#define TKZ_BPE_OVER 1  // 0: k_bpe_short / k_bpe_deferred always load both buckets
+#endif
+__device__ __forceinline__ const uint32_t* seg_over_stage(const DevTables& T, uint32_t* lds);
+
+// OV: launched with seg_over_lds(T) > 0 bytes of dynamic LDS for the bitmap
+template <bool COMPACT, bool OV>
 __global__ __launch_bounds__(256, TKZ_DEF_MINB) void k_bpe_deferred(DevTables T, const uint8_t* __restrict__ bytes, uint64_t limit,
                                                       Scratch S, Deferred D) {
     __shared__ uint32_t byte_id[256];
+    extern __shared__ uint32_t over_lds[];
     byte_id[threadIdx.x] = T.byte_id[threadIdx.x];
+    const uint32_t* ov = OV ? seg_over_stage(T, over_lds) : nullptr;
     __syncthreads();
     const uint64_t* list = T.dedup ? D.olist : D.list;
     const uint64_t n = D.cnt[T.dedup ? 1 : 0];
@@ -1556,41 +1637,137 @@ __global__ __launch_bounds__(256, TKZ_DEF_MINB) void k_bpe_deferred(DevTables T,
         if (lit) bpe_long_word<COMPACT>(T, byte_id, bytes, pos, ws, L, S);
         // register BPE: each width with the wave converged (chunk_commit)
         const bool r2 = valid && !lg && !lit && L <= 16, r4 = valid && !lg && !lit && L > 16;
-        if (__ballot(r2)) bpe_bucket_word<16, 2, COMPACT>(T, byte_id, bytes, limit, pos, ws, L, S, r2);
-        if (__ballot(r4)) bpe_bucket_word<16, 4, COMPACT>(T, byte_id, bytes, limit, pos, ws, L, S, r4);
+        if (__ballot(r2)) bpe_bucket_word<16, 2, COMPACT, OV>(T, byte_id, bytes, limit, pos, ws, L, S, r2, ov);
+        if (__ballot(r4)) bpe_bucket_word<16, 4, COMPACT, OV>(T, byte_id, bytes, limit, pos, ws, L, S, r4, ov);
     }
 }
 
 // k_bpe_short: the memo misses of <= 8 B that k_encode_blk leaves (round 6), listed per
-// chunk (chunk c's at slist[c << ch_log2 ..], D.scnt[c] of them). Persistent waves take
+// chunk (D.scnt[c] records at short_rec(S, chunk start, chunk bytes, i)). Persistent waves take
 // chunks c_first + wave + k * waves, sort the entries into two length-bucket LDS queues
 // (<= 4 B: 4-symbol register BPE, 5..8 B: 8 symbols: bpe.zig:213-253 rounds) and run a
 // bucket when 64 wait, one lane per word; results go to the chunks' dense areas
 // (chunk_commit). The old k_encode ran these queues inside the scan kernel, whose register
 // budget they set; here the scan kernel keeps its registers for resident waves.
-template <bool COMPACT>
-__global__ __launch_bounds__(256) void k_bpe_short(DevTables T, const uint8_t* __restrict__ bytes, uint64_t limit,
+//
+// A list entry carries the word's normalized bytes (its memo key k0, zero past L), which
+// k_encode_blk held in registers when it listed the miss: entry i of chunk c is one 16-B
+// record {pos | ord << POS_BITS | L << LEN_SHIFT, k0} (short_rec), written with one store.
+// The register BPE runs from the key and never reads the input bytes: that was a gather of
+// one 128-B line per word and a dependent round trip at the head of every bucket run.
+//
+// A chunk has up to one word per byte (1-byte docs, punctuation), so its list needs `cap`
+// records, cap = the chunk's bytes inside the scratch (2^ch_log2, less for the last chunk).
+// Its slice of offs (8 B per byte) holds the first cap / 2, its slices of ids and of tok (4 B
+// per byte each) the next cap / 4 each; on k_encode_blk's path all three are first written
+// by the kernels after k_bpe_short. Text with a delimiter between words stays in the first.
+__device__ __forceinline__ uint4* short_rec(const Scratch& S, uint64_t cs, uint32_t CB, uint32_t i) {
+    const uint32_t cap = (uint32_t)min((uint64_t)CB, S.tb - cs);  // (a multiple of 64)
+    uint64_t o = cs * 8 + (uint64_t)i * 16;
+    if (i >= cap / 2) o = S.tb * 8 + cs * 4 + (uint64_t)(i - cap / 2) * 16;
+    if (i >= cap / 4 * 3) o = S.tb * 16 + cs * 4 + (uint64_t)(i - cap / 4 * 3) * 16;
+    return (uint4*)(S.base + o);
+}
+
+#ifndef TKZ_SHORT_SHARED
+#define TKZ_SHORT_SHARED 0  // 1: block-shared queues (measured and not kept: DESIGN 13.4)
+#endif
+// OV: launched with seg_over_lds(T) > 0 bytes of dynamic LDS (one-bucket probes)
+// (compact: 5 blocks per CU = 5 waves per SIMD, i.e. <= 96 VGPRs; left alone it takes 98)
+template <bool COMPACT, bool OV>
+__global__ __launch_bounds__(256, COMPACT ? 5 : 1) void k_bpe_short(DevTables T, const uint8_t* __restrict__ bytes, uint64_t limit,
                                                    Scratch S, Deferred D, uint64_t c_first, uint64_t c_end,
                                                    uint32_t ch_log2) {
-    __shared__ uint64_t q[256 / WAVE][2][QCAP];
+    extern __shared__ uint32_t over_lds[];
+    const uint32_t* ov = OV ? seg_over_stage(T, over_lds) : nullptr;
     const int lane = lane_id(), wv = (int)(threadIdx.x >> 6);
     const uint64_t nwv = (uint64_t)gridDim.x * (256 / WAVE);
     uint32_t qn0 = 0, qn1 = 0;
-    auto run = [&](int b, uint32_t qb, uint32_t take) {
+#if TKZ_SHORT_SHARED
+    // Block-shared queues: the block's four waves take four consecutive chunks in lockstep
+    // and append to two block-level queues; when four full runs wait, every wave takes one
+    // (from the tail), so only the block's end runs partly filled buckets. The fill counts
+    // are block-uniform and live in every wave's registers: each wave publishes its two
+    // counts (cntw), all read them after an LDS barrier and place their entries at the
+    // prefix; a second barrier precedes the runs. A queue holds < 256 entries before an
+    // append (fewer than four full runs wait) and gets <= 256 more.
+    constexpr uint32_t QS = 512;
+    __shared__ uint4 qs[2][QS];
+    __shared__ uint32_t cntw[256 / WAVE];
+    auto runs = [&](int b, uint32_t qb, uint32_t take) {
         const bool act = (uint32_t)lane < take;
-        const uint64_t e = act ? q[wv][b][qb + lane] : 0ull;
+        uint4 r = make_uint4(0u, 0u, 0u, 0u);
+        if (act) r = qs[b][qb + lane];
+        const uint64_t e = ((uint64_t)r.y << 32) | r.x, k0 = ((uint64_t)r.w << 32) | r.z;
         const uint64_t pos = e & POS_MASK;
         const uint64_t ws = S.slot(pos, (uint32_t)(e >> POS_BITS) & ORD_MASK);
         const uint32_t L = (uint32_t)(e >> LEN_SHIFT);
-        if (b == 0) bpe_bucket_word<4, 1, COMPACT>(T, T.byte_id, bytes, limit, pos, ws, L, S, act);
-        else bpe_bucket_word<8, 1, COMPACT>(T, T.byte_id, bytes, limit, pos, ws, L, S, act);
+        if (b == 0) bpe_keyed_word<4, COMPACT, OV>(T, T.byte_id, bytes, k0, pos, ws, L, S, act, ov);
+        else bpe_keyed_word<8, COMPACT, OV>(T, T.byte_id, bytes, k0, pos, ws, L, S, act, ov);
+    };
+    for (uint64_t cb = c_first + (uint64_t)blockIdx.x * (256 / WAVE); cb < c_end; cb += nwv) {
+        uint32_t nmax = 0, n = 0;  // (nmax: the same in every wave)
+        for (int k = 0; k < 256 / WAVE; ++k) {
+            const uint32_t nk = cb + (uint64_t)k < c_end ? D.scnt[cb + (uint64_t)k] : 0u;
+            nmax = max(nmax, nk);
+            n = k == wv ? nk : n;
+        }
+        const uint64_t c = cb + (uint64_t)wv;
+        for (uint32_t j = 0; j < nmax; j += WAVE) {
+            const bool act = j + (uint32_t)lane < n;
+            uint4 r = make_uint4(0u, 0u, 0u, 0u);
+            if (act) r = *short_rec(S, c << ch_log2, 1u << ch_log2, j + (uint32_t)lane);
+            const uint32_t L = r.y >> (LEN_SHIFT - 32);
+            const uint64_t m0 = __ballot(act && L <= 4u), m1 = __ballot(act && L > 4u);
+            if (lane == 0) cntw[wv] = (uint32_t)__popcll(m0) | ((uint32_t)__popcll(m1) << 16);
+            EB_SYNC();
+            uint32_t pre = 0, tot = 0;
+#pragma unroll
+            for (int k = 0; k < 256 / WAVE; ++k) {
+                const uint32_t v = cntw[k];
+                pre += k < wv ? v : 0u;
+                tot += v;
+            }
+            if (act && L <= 4u) qs[0][qn0 + (pre & 0xFFFFu) + lanes_below(m0)] = r;
+            if (act && L > 4u) qs[1][qn1 + (pre >> 16) + lanes_below(m1)] = r;
+            qn0 += tot & 0xFFFFu;
+            qn1 += tot >> 16;
+            EB_SYNC();
+            while ((qn0 >> 6) + (qn1 >> 6) >= 4u) {  // (block-uniform)
+                const uint32_t t0 = min(qn0 >> 6, 4u);
+                if ((uint32_t)wv < t0) runs(0, qn0 - 64u * ((uint32_t)wv + 1u), WAVE);
+                else runs(1, qn1 - 64u * ((uint32_t)wv - t0 + 1u), WAVE);
+                qn0 -= 64u * t0;
+                qn1 -= 64u * (4u - t0);
+            }
+        }
+    }
+    // the block's end: the full runs left (< 4) and the two partly filled ones
+    const uint32_t n0 = (qn0 + 63u) >> 6, n1 = (qn1 + 63u) >> 6;
+    for (uint32_t t = (uint32_t)wv; t < n0 + n1; t += 256 / WAVE) {
+        if (t < n0) runs(0, 64u * t, min(64u, qn0 - 64u * t));
+        else runs(1, 64u * (t - n0), min(64u, qn1 - 64u * (t - n0)));
+    }
+#else
+    __shared__ uint64_t q[256 / WAVE][2][QCAP];   // entries
+    __shared__ uint64_t qk[256 / WAVE][2][QCAP];  // their keys
+    auto run = [&](int b, uint32_t qb, uint32_t take) {
+        const bool act = (uint32_t)lane < take;
+        const uint64_t e = act ? q[wv][b][qb + lane] : 0ull;
+        const uint64_t k0 = act ? qk[wv][b][qb + lane] : 0ull;
+        const uint64_t pos = e & POS_MASK;
+        const uint64_t ws = S.slot(pos, (uint32_t)(e >> POS_BITS) & ORD_MASK);
+        const uint32_t L = (uint32_t)(e >> LEN_SHIFT);
+        if (b == 0) bpe_keyed_word<4, COMPACT, OV>(T, T.byte_id, bytes, k0, pos, ws, L, S, act, ov);
+        else bpe_keyed_word<8, COMPACT, OV>(T, T.byte_id, bytes, k0, pos, ws, L, S, act, ov);
     };
     for (uint64_t c = c_first + (uint64_t)blockIdx.x * (256 / WAVE) + (uint64_t)wv; c < c_end; c += nwv) {
         const uint32_t n = D.scnt[c];
-        const uint64_t* src = D.slist + (c << ch_log2);
         for (uint32_t j = 0; j < n; j += WAVE) {
             const bool act = j + (uint32_t)lane < n;
-            const uint64_t e = act ? src[j + lane] : 0ull;
+            uint4 r = make_uint4(0u, 0u, 0u, 0u);
+            if (act) r = *short_rec(S, c << ch_log2, 1u << ch_log2, j + (uint32_t)lane);
+            const uint64_t e = ((uint64_t)r.y << 32) | r.x, k0 = ((uint64_t)r.w << 32) | r.z;
             const uint32_t L = (uint32_t)(e >> LEN_SHIFT);
             if (T.chain) {  // a new_id == first merge: the literal loop
                 if (act) bpe_long_word<COMPACT>(T, T.byte_id, bytes, e & POS_MASK,
@@ -1598,8 +1775,8 @@ __global__ __launch_bounds__(256) void k_bpe_short(DevTables T, const uint8_t* _
                 continue;
             }
             const uint64_t m0 = __ballot(act && L <= 4u), m1 = __ballot(act && L > 4u);
-            if (act && L <= 4u) q[wv][0][qn0 + lanes_below(m0)] = e;
-            if (act && L > 4u) q[wv][1][qn1 + lanes_below(m1)] = e;
+            if (act && L <= 4u) { q[wv][0][qn0 + lanes_below(m0)] = e; qk[wv][0][qn0 + lanes_below(m0)] = k0; }
+            if (act && L > 4u) { q[wv][1][qn1 + lanes_below(m1)] = e; qk[wv][1][qn1 + lanes_below(m1)] = k0; }
             qn0 += (uint32_t)__popcll(m0);
             qn1 += (uint32_t)__popcll(m1);
             WAVE_SYNC();
@@ -1610,6 +1787,7 @@ __global__ __launch_bounds__(256) void k_bpe_short(DevTables T, const uint8_t* _
     }
     if (qn0) run(0, 0, qn0);
     if (qn1) run(1, 0, qn1);
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -5000,15 +5178,6 @@ struct EbSmem {
 #ifndef TKZ_BLK_ABL
 #define TKZ_BLK_ABL 0
 #endif
-// k_encode_blk's barrier: orders the block's LDS traffic only. __syncthreads() is also a
-// workgroup release of global memory (s_waitcnt vmcnt(0)): every barrier waited for the
-// wave's outstanding record / token stores of the previous phase
-#define EB_SYNC()                                                         \
-    do {                                                                  \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");   \
-        __builtin_amdgcn_s_barrier();                                     \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");   \
-    } while (0)
 #ifndef TKZ_BLK_DOCPF
 #define TKZ_BLK_DOCPF 1  // k_encode_blk: the next chunk's chunk_doc / doc_off loaded during this chunk's words
 #endif
@@ -5312,7 +5481,7 @@ __global__ __launch_bounds__(EB_T, TKZ_BLK_MINW) void k_encode_blk(DevTables T, 
                 const uint32_t en = (open && ord == n_st - 1u) ? open_end : (e32 >> 16);
                 L = en - s;
                 pos = cs + s;
-                if (memo && L <= 16u) {
+                if ((memo || MODEL == 1) && L <= 16u) {  // (BPE: a short miss's list entry carries k0)
                     const uint32_t a = s >> 3, sh = (s & 7u) * 8u;
                     const uint64_t q0 = sm.stage[a], q1 = sm.stage[a + 1], q2 = sm.stage[a + 2];
                     k0 = sh ? (q0 >> sh) | (q1 << (64u - sh)) : q0;
@@ -5392,7 +5561,9 @@ __global__ __launch_bounds__(EB_T, TKZ_BLK_MINW) void k_encode_blk(DevTables T, 
                     uint32_t b = 0;
                     if (lane == 0) b = atomicAdd(&sm.sfill, (uint32_t)__popcll(ms));
                     b = rfl(b);
-                    if (dl == SQ) D.slist[cs + b + lanes_below(ms)] = ent;
+                    if (dl == SQ)
+                        *short_rec(S, cs, CB, b + lanes_below(ms)) = make_uint4(
+                            (uint32_t)ent, (uint32_t)(ent >> 32), (uint32_t)k0, (uint32_t)(k0 >> 32));
                 }
                 const uint64_t m = __ballot(dl == DQ);
                 if (dl == DQ) sm.q[wv][DQ][qn[DQ] + lanes_below(m)] = ent;
@@ -5446,13 +5617,14 @@ __global__ __launch_bounds__(EB_T, TKZ_BLK_MINW) void k_encode_blk(DevTables T, 
                 const uint32_t Lk = min(max(L, 1u), 16u);
                 bool hit = false;
                 uint32_t hmeta = 0, hw = 0, ht1 = 0, ht2 = 0;
+                // the normalized key (zero past L): the memo's, and a short miss's list entry
+                const uint32_t a = s0 >> 3, sh = (s0 & 7u) * 8u;
+                const uint64_t q0 = sm.stage[a], q1 = sm.stage[a + 1], q2 = sm.stage[a + 2];
+                uint64_t k0 = sh ? (q0 >> sh) | (q1 << (64u - sh)) : q0;
+                uint64_t k1 = sh ? (q1 >> sh) | (q2 << (64u - sh)) : q1;
+                k0 &= (2ull << (8u * min(Lk, 8u) - 1u)) - 1u;
+                k1 = Lk > 8u ? k1 & ((2ull << (8u * (Lk - 8u) - 1u)) - 1u) : 0ull;
                 if (memo) {
-                    const uint32_t a = s0 >> 3, sh = (s0 & 7u) * 8u;
-                    const uint64_t q0 = sm.stage[a], q1 = sm.stage[a + 1], q2 = sm.stage[a + 2];
-                    uint64_t k0 = sh ? (q0 >> sh) | (q1 << (64u - sh)) : q0;
-                    uint64_t k1 = sh ? (q1 >> sh) | (q2 << (64u - sh)) : q1;
-                    k0 &= (2ull << (8u * min(Lk, 8u) - 1u)) - 1u;
-                    k1 = Lk > 8u ? k1 & ((2ull << (8u * (Lk - 8u) - 1u)) - 1u) : 0ull;
                     const bool s8 = COMPACT && Lk <= 8u;
                     uint32_t h = short_key_hash(k0, k1, Lk) >> (32 - (s8 ? T.memo8_bits : T.memo_bits));
                     bool pend = act && L <= 16u;
@@ -5514,7 +5686,9 @@ __global__ __launch_bounds__(EB_T, TKZ_BLK_MINW) void k_encode_blk(DevTables T, 
                     uint32_t b = 0;
                     if (lane == 0) b = atomicAdd(&sm.sfill, (uint32_t)__popcll(mss));
                     b = rfl(b);
-                    if (miss && L <= 8u) D.slist[cs + b + lanes_below(mss)] = ent;
+                    if (miss && L <= 8u)
+                        *short_rec(S, cs, CB, b + lanes_below(mss)) = make_uint4(
+                            (uint32_t)ent, (uint32_t)(ent >> 32), (uint32_t)k0, (uint32_t)(k0 >> 32));
                 }
                 if (msd) {
                     if (miss && L > 8u) sm.q[wv][DQ][qn[DQ] + lanes_below(msd)] = ent;
@@ -6124,10 +6298,10 @@ static WsLayout layout(void* ws, uint64_t total_bytes, uint64_t n_docs, int seg 
     L.D.long_bytes = L.hdr + HDR_LONGB;
     L.D.scnt = (uint32_t*)p;
     p += align_up(nc * 4, 256);
-    // the short-miss lists live in the scratch's offs array (8 B per input byte: chunk c's at
-    // offs[c << ch_log2 ..], at most one word per byte): k_encode_blk runs only where nothing
-    // writes offs before k_bpe_short has read them (compact or T.mid tokens, no chain merge)
-    L.D.slist = (uint64_t*)L.S.base;
+    // the short-miss lists live in the scratch itself (short_rec: 16-B records in the chunk's
+    // slice of offs, past half the chunk's bytes in its slices of ids and tok): k_encode_blk
+    // runs only where nothing writes those arrays before k_bpe_short has read them (compact or
+    // T.mid tokens, no chain merge).
     L.partials = (uint64_t*)p;
     const uint64_t nb = (nc + SCAN_CHUNK - 1) / SCAN_CHUNK + 1;
     p += align_up(nb * 8, 256) + 1024;
@@ -6266,19 +6440,32 @@ static int deferred_grid() {
 #endif
 // grid of k_bpe_short: its resident blocks (persistent waves over the chunks: a second
 // round of blocks would start its chunks late)
-template <bool COMPACT>
-static int short_grid() {
-    static std::atomic<int> cache[MAX_DEVICES];
+// (dyn_lds: the overflow bitmap's bytes, 0 or a power of two up to 16 KiB: one cache entry each)
+template <bool COMPACT, bool OV>
+static int short_grid(size_t dyn_lds) {
+    static std::atomic<int> cache[MAX_DEVICES][16];
     const int dev = current_device();
-    int g = cache[dev].load(std::memory_order_relaxed);
+    int slot = 0;
+    while (slot < 15 && ((size_t)1 << slot) < dyn_lds) ++slot;
+    int g = cache[dev][slot].load(std::memory_order_relaxed);
     if (g == 0) {
         int per = 4;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_bpe_short<COMPACT>, 256, 0) != hipSuccess || per < 1)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_bpe_short<COMPACT, OV>, 256, dyn_lds) != hipSuccess ||
+            per < 1)
             per = 4;
         g = device_cus(dev) * per;
-        cache[dev].store(g, std::memory_order_relaxed);
+        cache[dev][slot].store(g, std::memory_order_relaxed);
     }
     return g;
+}
+// one-bucket probes in k_bpe_short / k_bpe_deferred: the compact table with a bitmap that fits LDS
+// (at least the one word seg_over_stage copies for a table of < 32 buckets)
+// TKZ_TWO_BUCKET=1 in the environment (read per launch: tests switch it) keeps the
+// two-bucket instantiations, as a table without a bitmap does.
+inline size_t bpe_over_lds(const DevTables& T) {
+    const char* two = getenv("TKZ_TWO_BUCKET");
+    const size_t n = TKZ_BPE_OVER && T.compact && !(two && two[0] == '1') ? seg_over_lds(T) : 0;
+    return n ? (n < 4 ? 4 : n) : 0;
 }
 #ifndef TKZ_BLK
 #define TKZ_BLK 1  // splitting pretokenizers: k_encode_blk (0: k_encode's persistent waves)
@@ -6321,8 +6508,15 @@ static hipError_t launch_main(const DevTables& T, const uint8_t* bytes, const ui
                            n_docs, limit, ch_log2, (const uint64_t*)W.chunk_doc, W.hdr, W.S, W.chunk_words,
                            W.doc_word, W.D, status);
         if (MODEL == 1) {
-            hipLaunchKernelGGL((k_bpe_short<COMPACT>), dim3((unsigned)short_grid<COMPACT>()), dim3(256), 0, st, T, bytes, limit,
-                               W.S, W.D, (uint64_t)0, (uint64_t)W.n_chunks, ch_log2);
+            const size_t ol = COMPACT ? bpe_over_lds(T) : 0;
+            if (COMPACT && ol)
+                hipLaunchKernelGGL((k_bpe_short<COMPACT, COMPACT>), dim3((unsigned)short_grid<COMPACT, COMPACT>(ol)),
+                                   dim3(256), ol, st, T, bytes, limit, W.S, W.D, (uint64_t)0, (uint64_t)W.n_chunks,
+                                   ch_log2);
+            else
+                hipLaunchKernelGGL((k_bpe_short<COMPACT, false>), dim3((unsigned)short_grid<COMPACT, false>(0)),
+                                   dim3(256), 0, st, T, bytes, limit, W.S, W.D, (uint64_t)0, (uint64_t)W.n_chunks,
+                                   ch_log2);
         }
         return hipGetLastError();
     }
@@ -6422,10 +6616,13 @@ static hipError_t encode_pass(const DevTables& T, const uint8_t* d_bytes, const 
             hipLaunchKernelGGL(k_dedup, dim3(dgrid), dim3(256), 0, st, T, d_bytes, limit, W.D,
                                (uint64_t)TKZ_DEDUP_FIRST, 1);
         }
-        if (T.compact)
-            hipLaunchKernelGGL(k_bpe_deferred<true>, dim3(dgrid), dim3(256), 0, st, T, d_bytes, limit, W.S, W.D);
+        const size_t ol = bpe_over_lds(T);  // (compact tables only)
+        if (T.compact && ol)
+            hipLaunchKernelGGL((k_bpe_deferred<true, true>), dim3(dgrid), dim3(256), ol, st, T, d_bytes, limit, W.S, W.D);
+        else if (T.compact)
+            hipLaunchKernelGGL((k_bpe_deferred<true, false>), dim3(dgrid), dim3(256), 0, st, T, d_bytes, limit, W.S, W.D);
         else
-            hipLaunchKernelGGL(k_bpe_deferred<false>, dim3(dgrid), dim3(256), 0, st, T, d_bytes, limit, W.S, W.D);
+            hipLaunchKernelGGL((k_bpe_deferred<false, false>), dim3(dgrid), dim3(256), 0, st, T, d_bytes, limit, W.S, W.D);
         // long words: one wavefront each (the grid drains the list; idle blocks exit at once);
         // the segmented path first, k_bpe_long on what it leaves
         if (W.G.ctr) {  // the segmented path, then k_bpe_long on the pretokens it leaves

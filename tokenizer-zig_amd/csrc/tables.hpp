@@ -49,10 +49,16 @@ TKZ_HD uint32_t merge_slot_wide(uint64_t key, uint32_t bits) { return (uint32_t)
 // Compact merge table: bucketized cuckoo hash. Bucket = 16 B = two 8-B slots
 // {a<<16|b, rank<<16|new_id}; every key sits in one of its two buckets (2^bits buckets,
 // load <= 1/2), so a lookup is exactly two 16-B loads issued together, never a chain.
+// (the two halves on their own: a one-bucket probe computes the second only where the
+// overflow bitmap sends it there)
+TKZ_HD uint32_t merge_bucket1_compact(uint32_t key, uint32_t bits) { return (key * 0x9E3779B1u) >> (32 - bits); }
+TKZ_HD uint32_t merge_bucket2_compact(uint32_t key, uint32_t bits, uint32_t b1) {
+    const uint32_t b2 = fmix32(key ^ 0x5bd1e995u) >> (32 - bits);
+    return b2 == b1 ? b1 ^ 1u : b2;
+}
 TKZ_HD void merge_buckets_compact(uint32_t key, uint32_t bits, uint32_t& b1, uint32_t& b2) {
-    b1 = (key * 0x9E3779B1u) >> (32 - bits);
-    b2 = fmix32(key ^ 0x5bd1e995u) >> (32 - bits);
-    if (b2 == b1) b2 = b1 ^ 1u;
+    b1 = merge_bucket1_compact(key, bits);
+    b2 = merge_bucket2_compact(key, bits, b1);
 }
 TKZ_HD uint32_t merge_match_compact(const uint4& p, const uint4& q, uint32_t key) {
     uint32_t v = NONE;
