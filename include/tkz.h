@@ -169,6 +169,79 @@ int tkz_pad_batch_device(tkz_tokenizer* tk, const uint64_t* d_row_ptr, const uin
                          tkz_offset* d_offsets2, uint32_t* d_type_ids, uint32_t* d_special_mask,
                          uint32_t* d_attention_mask, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sequence packing: CSR batch -> fixed-length training rows --------------------
+ * The batched counterpart of Encoding.mergeWith (src/encoding.zig:520-583): the docs of a
+ * CSR batch are concatenated into one token stream, each with an optional BOS in front and
+ * EOS behind, and the stream is cut every seq_len tokens into a dense [n_rows, seq_len]
+ * tensor of ids (documents span rows freely). With kb / ke = 1 if there is a BOS / EOS
+ * (else 0), k = kb + ke and len[d] = row_ptr[d+1] - row_ptr[d]:
+ *   doc d starts at stream position s[d] = (row_ptr[d] - row_ptr[0]) + d*k (row_ptr[0] may
+ *   be non-zero: a sub-range of a larger CSR); the stream has T = s[n_docs] tokens and fills
+ *   n_rows = ceil(T / seq_len) rows (T == 0: no rows, nothing written).
+ *   Position p < T belongs to the doc d with s[d] <= p < s[d+1] (an empty doc with k == 0
+ *   holds no position; with k > 0 it still contributes its BOS / EOS); with j = p - s[d]:
+ *   ids[p] = bos_id if j < kb, ids[row_ptr[d] + j - kb] if j < kb + len[d], else eos_id;
+ *   segment_ids[p] = d, position_ids[p] = j.
+ *   Position p >= T (the tail of the last row): ids[p] = pad_id, segment_ids[p] = TKZ_NO_ID,
+ *   position_ids[p] = 0.
+ *   doc_pos[d] = s[d] for d in 0..n_docs (the stream's "cu_seqlens"). */
+typedef struct tkz_pack_params {
+    uint64_t seq_len;      /* >= 1 */
+    uint32_t bos_id;       /* TKZ_NO_ID: none */
+    uint32_t eos_id;       /* TKZ_NO_ID: none */
+    uint32_t pad_id;
+    int id_width;          /* bytes per packed id: 4, or 2 when every id fits 16 bits */
+    int want_segments;     /* tkz_encode_pack_batch: also return segment_ids / position_ids / */
+    int want_positions;    /* doc_pos (the device entry point takes pointers instead)        */
+    int want_doc_pos;
+} tkz_pack_params;
+/* seq_len 2048, no BOS, no EOS, pad 0, id_width 4, flags off. */
+void tkz_pack_params_default(tkz_pack_params* params);
+/* ceil((n_tokens + n_docs*k) / seq_len): the rows a batch of n_tokens tokens packs into.
+ * With total_bytes as n_tokens it bounds the rows of any encode of those bytes (tokens never
+ * exceed bytes). 0 on invalid params. */
+uint64_t tkz_pack_rows(const tkz_pack_params* params, size_t n_docs, uint64_t n_tokens);
+/* Stream positions one thread block of the pack kernel emits per step (tests, tools). */
+size_t tkz_pack_tile(void);
+/* Packs a device-resident CSR batch on `stream` (NULL = the tokenizer's own), asynchronous,
+ * no allocation. d_row_ptr / d_ids may be the outputs of a tkz_encode_batch_device call
+ * queued on the same stream with no sync in between; the outputs must not alias them.
+ *   d_out_ids:      rows_capacity * seq_len elements of id_width bytes, 16-byte aligned
+ *   d_segment_ids / d_position_ids: rows_capacity * seq_len uint32, 16-byte aligned, or NULL
+ *   d_doc_pos:      n_docs + 1 uint64, or NULL
+ *   d_counts:       two uint64 (written): [0] = n_rows, [1] = T
+ *   d_status:       one uint32 set to TKZ_ERR_INVALID_ARGUMENT on a device-detected error;
+ *                   zero it before the call. Errors: n_rows > rows_capacity (only the first
+ *                   rows_capacity rows are written), or with id_width 2 an input id >= 65536.
+ * The params' want_* flags are ignored here. Fails with TKZ_ERR_INVALID_ARGUMENT, before any
+ * device use, on NULL params, seq_len == 0, id_width other than 2 or 4, and id_width 2 when
+ * the model vocab holds an id >= 65536 or a given bos_id / eos_id / pad_id is >= 65536.
+ * Truncation / padding settings do not apply (chain tkz_pad_batch_device for them). */
+int tkz_pack_batch_device(tkz_tokenizer* tk, const uint64_t* d_row_ptr, const uint32_t* d_ids, size_t n_docs,
+                          const tkz_pack_params* params, uint64_t rows_capacity, void* d_out_ids,
+                          uint32_t* d_segment_ids, uint32_t* d_position_ids, uint64_t* d_doc_pos,
+                          uint64_t* d_counts, uint32_t* d_status, void* stream);
+/* Packed rows of a host batch. Arrays are library-allocated; free with tkz_packed_free.
+ * Arrays that were not asked for are NULL. */
+typedef struct tkz_packed {
+    size_t n_docs;
+    uint64_t n_tokens;       /* T: stream tokens, separators included, padding not */
+    uint64_t n_rows;
+    uint64_t seq_len;
+    int id_width;
+    void* ids;               /* [n_rows * seq_len] of id_width bytes */
+    uint32_t* segment_ids;   /* [n_rows * seq_len] */
+    uint32_t* position_ids;  /* [n_rows * seq_len] */
+    uint64_t* doc_pos;       /* [n_docs + 1] */
+} tkz_packed;
+/* tkz_encode_batch's encode of host-resident docs, packed on the device; only the packed
+ * arrays asked for cross PCIe (2 or 4 bytes per token against the CSR's 12). Not chunk-
+ * pipelined. Fails with TKZ_ERR_INVALID_ARGUMENT like tkz_pack_batch_device, and also when
+ * truncation or padding is enabled on the tokenizer. */
+int tkz_encode_pack_batch(tkz_tokenizer* tk, const uint8_t* bytes, const uint64_t* doc_off, size_t n_docs,
+                          const tkz_pack_params* params, tkz_packed* out);
+void tkz_packed_free(tkz_packed* p);
+
 /* Batched encode of DEVICE-resident docs on `stream` (a hipStream_t, NULL = the
  * tokenizer's own stream). No allocation.
  *   d_bytes:   total_bytes bytes, buffer readable up to a multiple of 16 bytes

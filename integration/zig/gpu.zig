@@ -190,6 +190,28 @@ pub const GpuTokenizer = struct {
         c.tkz_batch_free(b);
     }
 
+    /// encodeBatch packed on the GPU into dense [n_rows, seq_len] training rows: the docs
+    /// concatenated (Encoding.mergeWith over the batch, encoding.zig:520-583) with the
+    /// params' BOS / EOS around each and the stream cut every seq_len tokens; ids of 4 or 2
+    /// bytes, segment / position ids and doc_pos when the params ask for them (layout in
+    /// tkz.h, tkz_pack_params). Start from packParams(); free with freePacked.
+    pub fn encodePacked(self: *Self, bytes: []const u8, doc_off: []const u64, params: c.tkz_pack_params) Error!c.tkz_packed {
+        var out: c.tkz_packed = undefined;
+        try check(c.tkz_encode_pack_batch(self.h, bytes.ptr, doc_off.ptr, doc_off.len - 1, &params, &out));
+        return out;
+    }
+
+    /// tkz_pack_params_default: seq_len 2048, no BOS / EOS (c.TKZ_NO_ID), pad 0, 4-byte ids.
+    pub fn packParams() c.tkz_pack_params {
+        var p: c.tkz_pack_params = undefined;
+        c.tkz_pack_params_default(&p);
+        return p;
+    }
+
+    pub fn freePacked(_: *Self, p: *c.tkz_packed) void {
+        c.tkz_packed_free(p);
+    }
+
     /// Decodes every row of a CSR batch on the GPU; free with freeTextBatch.
     pub fn decodeBatch(self: *Self, row_ptr: []const u64, ids: []const u32, skip_special_tokens: bool) Error!c.tkz_text_batch {
         var out: c.tkz_text_batch = undefined;

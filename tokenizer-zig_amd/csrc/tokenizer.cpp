@@ -21,6 +21,7 @@
 #include "decode.hpp"
 #include "encode.hpp"
 #include "json.hpp"
+#include "pack.hpp"
 #include "pad.hpp"
 #include "span.hpp"
 #include "tables.hpp"
@@ -200,6 +201,12 @@ struct DeviceState {
     uint64_t* d_offs2 = nullptr; size_t cap_offs2 = 0;
     uint32_t* d_masks = nullptr; size_t cap_masks = 0;  // type_ids | special | attention
     uint8_t* d_pad_ws = nullptr; size_t cap_pad_ws = 0;
+    // packed rows of the host-buffer API (tkz_encode_pack_batch)
+    uint8_t* d_pk_ids = nullptr; size_t cap_pk_ids = 0;    // id_width bytes per position
+    uint32_t* d_pk_seg = nullptr; size_t cap_pk_seg = 0;
+    uint32_t* d_pk_pos = nullptr; size_t cap_pk_pos = 0;
+    uint64_t* d_pk_doc = nullptr; size_t cap_pk_doc = 0;
+    uint64_t* d_pk_cnt = nullptr; size_t cap_pk_cnt = 0;
     // FastTokenizer span batches of the host-buffer API
     uint8_t* d_fast_ws = nullptr; size_t cap_fast_ws = 0;
     uint32_t* d_span = nullptr; size_t cap_span = 0;  // len | ids | attention
@@ -1484,7 +1491,8 @@ void tkz_destroy(tkz_tokenizer* t) {
                         (void*)d.d_status, (void*)d.d_dec_ids, (void*)d.d_dec_row, (void*)d.d_dec_out,
                         (void*)d.d_dec_off, (void*)d.d_dec_ws, (void*)d.d_row2, (void*)d.d_ids2, (void*)d.d_offs2,
                         (void*)d.d_masks, (void*)d.d_pad_ws, (void*)d.d_fast_ws, (void*)d.d_span,
-                        (void*)d.d_span_offs})
+                        (void*)d.d_span_offs, (void*)d.d_pk_ids, (void*)d.d_pk_seg, (void*)d.d_pk_pos,
+                        (void*)d.d_pk_doc, (void*)d.d_pk_cnt})
             if (p) hipFree(p);
         for (auto& tm : d.timers) for (auto& e : tm.ev) if (e) hipEventDestroy(e);
         for (hipEvent_t e : d.chunk_ev) hipEventDestroy(e);
@@ -2322,6 +2330,132 @@ int tkz_pad_batch_device(tkz_tokenizer* t, const uint64_t* d_row_ptr, const uint
                                    (uint64_t*)d_offsets2, d_type_ids, d_special_mask, d_attention_mask, d_workspace,
                                    st);
     if (e != hipSuccess) return fail(TKZ_ERR_DEVICE, std::string("pad launch failed: ") + hipGetErrorString(e));
+    return TKZ_OK;
+}
+
+// ---- sequence packing (pack.hip) ----
+void tkz_pack_params_default(tkz_pack_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->seq_len = 2048;
+    p->bos_id = TKZ_NO_ID;
+    p->eos_id = TKZ_NO_ID;
+    p->id_width = 4;
+}
+
+static tkz::PackParams pack_params(const tkz_pack_params& p) {
+    return tkz::PackParams{p.seq_len, p.bos_id, p.eos_id, p.pad_id, p.id_width};
+}
+
+// Everything about a pack call that can be refused without a device.
+static int pack_validate(const tkz_tokenizer* t, const tkz_pack_params* p, size_t n_docs) {
+    if (!t || !p) return fail(TKZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (p->seq_len == 0) return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: seq_len must be at least 1");
+    if (p->id_width != 2 && p->id_width != 4) return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: id_width must be 2 or 4");
+    if (p->id_width == 2) {
+        if (!t->hostT.narrow) return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: id_width 2 but the vocab holds an id >= 65536");
+        if ((p->bos_id != TKZ_NO_ID && p->bos_id > 0xFFFFu) || (p->eos_id != TKZ_NO_ID && p->eos_id > 0xFFFFu) ||
+            p->pad_id > 0xFFFFu)
+            return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: id_width 2 but bos_id / eos_id / pad_id is >= 65536");
+    }
+    if ((uint64_t)n_docs >= 0xFFFFFFFFull) return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: too many docs for 32-bit segment ids");
+    return TKZ_OK;
+}
+
+uint64_t tkz_pack_rows(const tkz_pack_params* p, size_t n_docs, uint64_t n_tokens) {
+    if (!p || p->seq_len == 0) return 0;
+    return tkz::pack_rows(pack_params(*p), n_docs, n_tokens);
+}
+
+size_t tkz_pack_tile(void) { return tkz::PACK_TILE; }
+
+int tkz_pack_batch_device(tkz_tokenizer* t, const uint64_t* d_row_ptr, const uint32_t* d_ids, size_t n_docs,
+                          const tkz_pack_params* params, uint64_t rows_capacity, void* d_out_ids,
+                          uint32_t* d_segment_ids, uint32_t* d_position_ids, uint64_t* d_doc_pos, uint64_t* d_counts,
+                          uint32_t* d_status, void* stream) {
+    int rc = pack_validate(t, params, n_docs);
+    if (rc) return rc;
+    if (!d_row_ptr || !d_counts || !d_status || (rows_capacity && !d_out_ids) || (n_docs && !d_ids))
+        return fail(TKZ_ERR_INVALID_ARGUMENT, "null argument");
+    if (((uintptr_t)d_out_ids | (uintptr_t)d_segment_ids | (uintptr_t)d_position_ids) & 15)
+        return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: output arrays must be 16-byte aligned");
+    if (rows_capacity > (UINT64_MAX >> 3) / params->seq_len)
+        return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: rows_capacity * seq_len overflows");
+    std::lock_guard<std::mutex> g(t->mu);
+    if ((rc = ensure_device(t))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : t->dev.stream;
+    hipError_t e = tkz::launch_pack(pack_params(*params), d_row_ptr, d_ids, n_docs, rows_capacity, d_out_ids,
+                                    d_segment_ids, d_position_ids, d_doc_pos, d_counts, d_status,
+                                    TKZ_ERR_INVALID_ARGUMENT, st);
+    if (e != hipSuccess) return fail(TKZ_ERR_DEVICE, std::string("pack launch failed: ") + hipGetErrorString(e));
+    return TKZ_OK;
+}
+
+void tkz_packed_free(tkz_packed* p) {
+    if (!p) return;
+    out_free(p->ids); out_free(p->segment_ids); out_free(p->position_ids); out_free(p->doc_pos);
+    memset(p, 0, sizeof *p);
+}
+
+int tkz_encode_pack_batch(tkz_tokenizer* t, const uint8_t* bytes, const uint64_t* doc_off, size_t n_docs,
+                          const tkz_pack_params* params, tkz_packed* out) {
+    int rc = pack_validate(t, params, n_docs);
+    if (rc) return rc;
+    if (!doc_off || !out || (n_docs && !bytes && doc_off[n_docs] > 0)) return fail(TKZ_ERR_INVALID_ARGUMENT, "null argument");
+    memset(out, 0, sizeof *out);
+    std::lock_guard<std::mutex> g(t->mu);
+    if (t->pp.truncate || t->pp.pad)
+        return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: truncation / padding is enabled (pack the device CSR instead)");
+    uint64_t nt = 0;
+    if ((rc = encode_host_to_device(t, bytes, doc_off, n_docs, &nt))) return rc;
+    DeviceState& d = t->dev;
+    const tkz::PackParams P = pack_params(*params);
+    const uint64_t rows = tkz::pack_rows(P, n_docs, nt);  // exact: the token count is known here
+    if (rows > (UINT64_MAX >> 3) / P.seq_len) return fail(TKZ_ERR_INVALID_ARGUMENT, "pack: rows * seq_len overflows");
+    const uint64_t n_pos = rows * P.seq_len;
+    const size_t w = (size_t)P.id_width;
+    if ((rc = grow(d.d_pk_ids, d.cap_pk_ids, n_pos * w + 16)) || (rc = grow(d.d_pk_cnt, d.cap_pk_cnt, 2)) ||
+        (params->want_segments && (rc = grow(d.d_pk_seg, d.cap_pk_seg, n_pos + 4))) ||
+        (params->want_positions && (rc = grow(d.d_pk_pos, d.cap_pk_pos, n_pos + 4))) ||
+        (params->want_doc_pos && (rc = grow(d.d_pk_doc, d.cap_pk_doc, n_docs + 1))))
+        return rc;
+    hipStream_t st = d.stream;
+    hipError_t e = tkz::launch_pack(P, d.d_row, d.d_ids, n_docs, rows, d.d_pk_ids,
+                                    params->want_segments ? d.d_pk_seg : nullptr,
+                                    params->want_positions ? d.d_pk_pos : nullptr,
+                                    params->want_doc_pos ? d.d_pk_doc : nullptr, d.d_pk_cnt, d.d_status,
+                                    TKZ_ERR_INVALID_ARGUMENT, st);  // (d_status is 0: the encode was checked)
+    if (e != hipSuccess) return fail(TKZ_ERR_DEVICE, std::string("pack launch failed: ") + hipGetErrorString(e));
+    out->n_docs = n_docs;
+    out->n_rows = rows;
+    out->seq_len = P.seq_len;
+    out->id_width = P.id_width;
+    out->ids = out_alloc(std::max<uint64_t>(n_pos, 1) * w);
+    if (params->want_segments) out->segment_ids = (uint32_t*)out_alloc(std::max<uint64_t>(n_pos, 1) * 4);
+    if (params->want_positions) out->position_ids = (uint32_t*)out_alloc(std::max<uint64_t>(n_pos, 1) * 4);
+    if (params->want_doc_pos) out->doc_pos = (uint64_t*)out_alloc((n_docs + 1) * 8);
+    if (!out->ids || (params->want_segments && !out->segment_ids) || (params->want_positions && !out->position_ids) ||
+        (params->want_doc_pos && !out->doc_pos)) {
+        tkz_packed_free(out);
+        return fail(TKZ_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    uint64_t cnt[2] = {0, 0};
+    uint32_t status = 0;
+    hipMemcpyAsync(cnt, d.d_pk_cnt, 16, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(&status, d.d_status, 4, hipMemcpyDeviceToHost, st);
+    if (n_pos) {
+        hipMemcpyAsync(out->ids, d.d_pk_ids, n_pos * w, hipMemcpyDeviceToHost, st);
+        if (out->segment_ids) hipMemcpyAsync(out->segment_ids, d.d_pk_seg, n_pos * 4, hipMemcpyDeviceToHost, st);
+        if (out->position_ids) hipMemcpyAsync(out->position_ids, d.d_pk_pos, n_pos * 4, hipMemcpyDeviceToHost, st);
+    }
+    if (out->doc_pos) hipMemcpyAsync(out->doc_pos, d.d_pk_doc, (n_docs + 1) * 8, hipMemcpyDeviceToHost, st);
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { tkz_packed_free(out); return fail(TKZ_ERR_DEVICE, hipGetErrorString(e)); }
+    if (status || cnt[0] != rows) {
+        tkz_packed_free(out);
+        return fail(status ? (int)status : TKZ_ERR_DEVICE, "pack: device reported an error");
+    }
+    out->n_tokens = cnt[1];
     return TKZ_OK;
 }
 

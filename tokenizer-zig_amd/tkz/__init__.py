@@ -3,6 +3,22 @@ the C ABI of ``include/tkz.h`` (libtkz.so, built in-tree for gfx950).
 
 Encode always runs through the HIP kernels; if the library or a GPU is missing the
 encode calls raise — there is no CPU fallback on the product path.
+
+Sequence packing (tkz_pack_params in include/tkz.h states the exact layout): the docs of a
+batch are concatenated into one token stream, each with an optional BOS in front and EOS
+behind, and the stream is cut every ``seq_len`` tokens into dense ``[n_rows, seq_len]``
+rows, the tail of the last row filled with ``pad_id``.
+
+- ``Tokenizer.encode_pack(data, doc_off, seq_len, bos_id=None, eos_id=None, pad_id=0,
+  dtype=np.uint32, segments=False, positions=False, doc_pos=False)`` encodes host docs and
+  returns ``{"ids": [n_rows, seq_len] of dtype, "n_tokens": T}`` plus, when asked for,
+  ``"segment_ids"`` (doc index per position, 0xFFFFFFFF on padding), ``"position_ids"``
+  (index inside the doc's span, BOS included) and ``"doc_pos"`` (u64[n_docs + 1] stream
+  start of every doc). ``dtype=np.uint16`` halves the copy when the vocab fits 16 bits. Only
+  the packed arrays cross PCIe. Raises InvalidArgument with truncation / padding enabled.
+- ``DeviceBatch.pack(seq_len, ...)`` packs the CSR that ``DeviceBatch.run()`` left in HBM, on
+  the same stream with no sync in between, and returns a ``PackedBatch`` whose ``results()``
+  copies the rows back.
 """
 from __future__ import annotations
 
@@ -68,6 +84,42 @@ class _TextBatch(ctypes.Structure):
         ("offsets", ctypes.POINTER(ctypes.c_uint64)),
         ("bytes", ctypes.c_void_p),
     ]
+
+
+class _PackParams(ctypes.Structure):
+    _fields_ = [("seq_len", ctypes.c_uint64), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32),
+                ("pad_id", ctypes.c_uint32), ("id_width", ctypes.c_int), ("want_segments", ctypes.c_int),
+                ("want_positions", ctypes.c_int), ("want_doc_pos", ctypes.c_int)]
+
+
+class _Packed(ctypes.Structure):
+    _fields_ = [("n_docs", ctypes.c_size_t), ("n_tokens", ctypes.c_uint64), ("n_rows", ctypes.c_uint64),
+                ("seq_len", ctypes.c_uint64), ("id_width", ctypes.c_int), ("ids", ctypes.c_void_p),
+                ("segment_ids", ctypes.POINTER(ctypes.c_uint32)), ("position_ids", ctypes.POINTER(ctypes.c_uint32)),
+                ("doc_pos", ctypes.POINTER(ctypes.c_uint64))]
+
+
+NO_ID = 0xFFFFFFFF  # TKZ_NO_ID
+
+
+def pack_params(seq_len: int, bos_id: Optional[int] = None, eos_id: Optional[int] = None, pad_id: int = 0,
+                dtype=np.uint32, segments: bool = False, positions: bool = False,
+                doc_pos: bool = False) -> "_PackParams":
+    """tkz_pack_params from keyword form (None = no BOS / EOS; dtype uint32 or uint16)."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.uint32), np.dtype(np.uint16)):
+        raise ValueError("dtype must be np.uint32 or np.uint16")
+    if int(seq_len) < 0:
+        raise ValueError("seq_len must not be negative")
+    p = _PackParams()
+    lib().tkz_pack_params_default(ctypes.byref(p))
+    p.seq_len = int(seq_len)
+    p.bos_id = NO_ID if bos_id is None else int(bos_id)
+    p.eos_id = NO_ID if eos_id is None else int(eos_id)
+    p.pad_id = int(pad_id)
+    p.id_width = dt.itemsize
+    p.want_segments, p.want_positions, p.want_doc_pos = int(bool(segments)), int(bool(positions)), int(bool(doc_pos))
+    return p
 
 
 class _MemoInfo(ctypes.Structure):
@@ -142,6 +194,12 @@ def lib():
         "tkz_pad_capacity": (u64, [vp, sz, u64]),
         "tkz_pad_workspace_size": (sz, [sz]),
         "tkz_pad_batch_device": (c.c_int, [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "tkz_pack_params_default": (None, [c.POINTER(_PackParams)]),
+        "tkz_pack_rows": (u64, [c.POINTER(_PackParams), sz, u64]),
+        "tkz_pack_tile": (sz, []),
+        "tkz_pack_batch_device": (c.c_int, [vp, vp, vp, sz, c.POINTER(_PackParams), u64, vp, vp, vp, vp, vp, vp, vp]),
+        "tkz_encode_pack_batch": (c.c_int, [vp, vp, c.POINTER(u64), sz, c.POINTER(_PackParams), c.POINTER(_Packed)]),
+        "tkz_packed_free": (None, [c.POINTER(_Packed)]),
         "tkz_decode_workspace_size": (sz, [vp, sz, u64]),
         "tkz_decode_batch_device": (c.c_int, [vp, vp, vp, sz, u64, c.c_int, vp, u64, vp, vp, sz, vp]),
         "tkz_get_vocab_size": (sz, [vp]),
@@ -379,6 +437,42 @@ class Tokenizer:
             return row_ptr, ids, offs
         finally:
             self._lib.tkz_batch_free(ctypes.byref(b))
+
+    def encode_pack(self, data, doc_off, seq_len: int, bos_id: Optional[int] = None, eos_id: Optional[int] = None,
+                    pad_id: int = 0, dtype=np.uint32, segments: bool = False, positions: bool = False,
+                    doc_pos: bool = False) -> dict:
+        """encode_batch, packed on the device into [n_rows, seq_len] training rows
+        (tkz_encode_pack_batch; layout in the module docstring). Returns {"ids", "n_tokens"}
+        plus "segment_ids" / "position_ids" / "doc_pos" when asked for."""
+        p = pack_params(seq_len, bos_id, eos_id, pad_id, dtype, segments, positions, doc_pos)
+        data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
+        doc_off = _check_batch(data, doc_off)
+        n = len(doc_off) - 1
+        b = _Packed()
+        rc = self._lib.tkz_encode_pack_batch(self._h, data.ctypes.data_as(ctypes.c_void_p),
+                                             doc_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n,
+                                             ctypes.byref(p), ctypes.byref(b))
+        if rc:
+            _err(rc)
+        try:
+            rows, L = int(b.n_rows), int(b.seq_len)
+            dt = np.dtype(dtype)
+
+            def arr(ptr, ctype, shape, npdt):
+                if not shape[0]:
+                    return np.zeros(shape, dtype=npdt)
+                return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=shape).copy()
+            out = {"ids": arr(b.ids, ctypes.c_uint16 if dt.itemsize == 2 else ctypes.c_uint32, (rows, L), dt),
+                   "n_tokens": int(b.n_tokens)}
+            if segments:
+                out["segment_ids"] = arr(b.segment_ids, ctypes.c_uint32, (rows, L), np.uint32)
+            if positions:
+                out["position_ids"] = arr(b.position_ids, ctypes.c_uint32, (rows, L), np.uint32)
+            if doc_pos:
+                out["doc_pos"] = np.ctypeslib.as_array(b.doc_pos, shape=(n + 1,)).copy()
+            return out
+        finally:
+            self._lib.tkz_packed_free(ctypes.byref(b))
 
     # Tokenizer.decode (lib.zig:163-189)
     def decode(self, ids: Sequence[int], skip_special_tokens: bool = False) -> bytes:
@@ -751,12 +845,99 @@ class DeviceBatch:
             _err(rc)
         return int(t[0])
 
+    def pack(self, seq_len: int, bos_id: Optional[int] = None, eos_id: Optional[int] = None, pad_id: int = 0,
+             dtype=np.uint32, segments: bool = False, positions: bool = False, doc_pos: bool = False,
+             stream: Optional[int] = None, out: Optional["PackedBatch"] = None) -> "PackedBatch":
+        """Packs the CSR of the last run() into [n_rows, seq_len] rows on the device
+        (tkz_pack_batch_device), async on `stream` (the stream run() used: no sync is
+        needed in between). `out`: a PackedBatch of an earlier pack() whose buffers are
+        reused (its row capacity and arrays must cover this call)."""
+        p = pack_params(seq_len, bos_id, eos_id, pad_id, dtype, segments, positions, doc_pos)
+        cap = int(lib().tkz_pack_rows(ctypes.byref(p), self.n_docs, self.total))  # tokens never exceed bytes
+        if out is None:
+            out = PackedBatch(self.tok, self.n_docs, cap * int(seq_len), segments, positions, doc_pos)
+        out.launch(self.d_row.ptr, self.d_ids.ptr, self.n_docs, p, cap, np.dtype(dtype), segments, positions, doc_pos,
+                   stream)
+        return out
+
     def free(self):
         bufs = [self.d_row, self.d_ids, self.d_offs, self.d_ws, self.d_status]
         if self._own_inputs:
             bufs += [self.d_bytes, self.d_off]
         for b in bufs:
             b.free()
+
+
+class PackedBatch:
+    """Device-resident packed rows (tkz_pack_batch_device) for up to n_docs docs and n_pos
+    stream positions; ids are sized for 4-byte elements, so the same buffers serve a later
+    2-byte pack."""
+
+    def __init__(self, tok: Tokenizer, n_docs: int, n_pos: int, segments: bool, positions: bool, doc_pos: bool):
+        self.tok = tok
+        self.cap_docs = self.n_docs = int(n_docs)
+        self.cap_pos = int(n_pos)
+        self.d_ids = DeviceBuffer(self.cap_pos * 4 + 16)
+        self.d_seg = DeviceBuffer(self.cap_pos * 4 + 16) if segments else None
+        self.d_pos = DeviceBuffer(self.cap_pos * 4 + 16) if positions else None
+        self.d_doc = DeviceBuffer((self.cap_docs + 1) * 8) if doc_pos else None
+        self.d_counts = DeviceBuffer(16)
+        self.d_status = DeviceBuffer(16)
+        self.d_status.zero()  # (sticky: a PackedBatch that reported an error is not reused)
+        rc = lib().tkz_device_synchronize()
+        if rc:
+            _err(rc)
+
+    def launch(self, d_row: int, d_ids: int, n_docs: int, p: "_PackParams", rows_capacity: int, dtype, segments,
+               positions, doc_pos, stream: Optional[int]):
+        if rows_capacity * int(p.seq_len) > self.cap_pos or (doc_pos and n_docs > self.cap_docs):
+            raise TokenizerError(10, "PackedBatch: buffers too small for this pack")
+        if (segments and not self.d_seg) or (positions and not self.d_pos) or (doc_pos and not self.d_doc):
+            raise TokenizerError(10, "PackedBatch: an optional array asked for was not allocated")
+        self.n_docs, self.seq_len, self.dtype = int(n_docs), int(p.seq_len), dtype
+        self._want = (bool(segments), bool(positions), bool(doc_pos))
+        self.stream = stream
+        L = lib()
+        rc = L.tkz_pack_batch_device(self.tok.handle, d_row, d_ids, self.n_docs, ctypes.byref(p), rows_capacity,
+                                     self.d_ids.ptr, self.d_seg.ptr if segments else None,
+                                     self.d_pos.ptr if positions else None, self.d_doc.ptr if doc_pos else None,
+                                     self.d_counts.ptr, self.d_status.ptr, stream)
+        if rc:
+            _err(rc)
+
+    def results(self) -> dict:
+        """{"ids" [n_rows, seq_len], "n_tokens", optional arrays} copied back to the host,
+        after waiting for the device."""
+        rc = lib().tkz_device_synchronize() if self.stream else lib().tkz_synchronize(self.tok.handle)
+        if rc:
+            _err(rc)
+        st = np.zeros(4, dtype=np.uint32)
+        self.d_status.download(st)
+        if st[0]:
+            raise TokenizerError(int(st[0]), "device-reported error")
+        cnt = np.zeros(2, dtype=np.uint64)
+        self.d_counts.download(cnt)
+        rows, L = int(cnt[0]), self.seq_len
+        seg, pos, doc = self._want
+
+        def get(buf, dt):
+            a = np.zeros((rows, L), dtype=dt)
+            if a.size:
+                buf.download(a)
+            return a
+        out = {"ids": get(self.d_ids, self.dtype), "n_tokens": int(cnt[1])}
+        if seg:
+            out["segment_ids"] = get(self.d_seg, np.uint32)
+        if pos:
+            out["position_ids"] = get(self.d_pos, np.uint32)
+        if doc:
+            out["doc_pos"] = self.d_doc.download(np.zeros(self.n_docs + 1, dtype=np.uint64))
+        return out
+
+    def free(self):
+        for b in (self.d_ids, self.d_seg, self.d_pos, self.d_doc, self.d_counts, self.d_status):
+            if b is not None:
+                b.free()
 
 
 from .fast import FastTokenizer, FastTokenizerOptions, SpanBatch, SpanEncoding, SpanToken  # noqa: E402,F401
